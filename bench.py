@@ -4,12 +4,22 @@ project -> bin -> sort -> blend -> BGR8 frame path at 1920x1080 on a synthetic
 framebuffer's tile rows split into N bands, one per GPU, one RCCL all-gather
 per frame inside gs_render -- the row-band group of gs_group.hip).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  A "step" is one full frame.  The timed region
 covers K frames enqueued back to back (inputs resident in HBM), bracketed by a
 barrier + device synchronise; the value is K / max-over-ranks elapsed.
+
+A plain run does what that value needs and no more: scene, renderers, warm-up,
+the K timed frames, the result line (metric, value, unit, ms_per_step, the
+workload and the last timed frame's stats).  --full adds everything else the
+line can carry, each from passes of its own after the timed region: the check
+of the last timed frame against a blocking render, the end-to-end rate with
+readback, the one-in-flight kernel table, the roofline (with the measured copy
+peak, taken before the timed region), the single-frame latency, the group's
+per-band times and the CPU baselines.  --dump-outputs DIR writes the last timed
+frame as DIR/<name>.npy (dump_outputs).
 
 How the N GPUs are driven (launch_mode):
   N = 1 ("single"): F renderers (frames in flight) take frames round-robin on
@@ -53,6 +63,13 @@ def parse():
     # 20 timed frames after 5 / 30 / 200 warm-up frames ran at 6 700 / 6 950 /
     # 7 600 frames/s (one box, interleaved)
     ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: frame check, end-to-end rate, kernel table, roofline, frame latency, "
+                    "group band times and CPU baselines (passes of their own; the options below that size them "
+                    "apply only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed frame (what a caller of the timed path reads "
+                    "back) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -359,8 +376,41 @@ def frame_digest(bgr) -> str:
     return hashlib.sha1(bgr.tobytes()).hexdigest()[:16]
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # of --dump-outputs' 64 MB, the .npy headers and the small arrays aside
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(np, path: str, r, with_rgba: bool) -> dict:
+    """--dump-outputs: the frame renderer `r` rendered last, as a caller reads
+    it back -- bgr (getFrameBuffer: rows x W x 3, the 8-bit levels as
+    float32), histogram (getIPUHistogram: per-tile list lengths, float64) and,
+    for a single renderer, rgba (gs_read_rgba32f: rows x W x 4 float32).  The
+    per-pixel arrays together stay within DUMP_BUDGET_BYTES: a larger frame
+    (4K) is written as the same fixed, seeded sample of its pixels in each
+    (K x 3, K x 4), with the sampled pixels' row-major indices in
+    pixel_index (float64).  Returns {name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    out = {"bgr": r.get_frame_buffer().astype(np.float32), "histogram": r.get_histogram().astype(np.float64)}
+    if with_rgba:
+        out["rgba"] = np.ascontiguousarray(r.get_rgba(), np.float32)
+    px = out["bgr"].shape[0] * out["bgr"].shape[1]
+    per_px = 4 * (3 + (4 if with_rgba else 0))
+    if px * per_px > DUMP_BUDGET_BYTES:  # (a sampled pixel costs its 8-byte index too)
+        keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(px, DUMP_BUDGET_BYTES // (per_px + 8),
+                                                                      replace=False))
+        for k in ("bgr", "rgba"):
+            if k in out:
+                out[k] = np.ascontiguousarray(out[k].reshape(px, -1)[keep])
+        out["pixel_index"] = keep.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in out.items()}
+
+
 def main():
     a = parse()
+    if a.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if a.config5:
         a.n, a.width, a.height, a.seed, a.sh_degree = 8_000_000, 3840, 2160, 8, 0
     import numpy as np
@@ -476,8 +526,9 @@ def main():
             raise err
 
     # the achievable copy rate, measured before the timed region (its copies
-    # keep the GPU busy for ~0.1 s, as a long run's first frames would)
-    peak_measured = measured_copy_peak(torch, a.copy_peak_s)
+    # keep the GPU busy for ~0.1 s, as a long run's first frames would);
+    # the roofline's figure, so --full only
+    peak_measured = measured_copy_peak(torch, a.copy_peak_s) if a.full else None
     # pre-warm: untimed frames for --prewarm-ms (beyond the --warmup steps),
     # reported in the line
     prewarm = {"ms": a.prewarm_ms, "frames": 0,
@@ -516,6 +567,109 @@ def main():
         elapsed = float(t.item())
     fps = a.steps / elapsed
     ms_per_step = 1e3 * elapsed / a.steps
+
+    # PMC counters are per launch (kernel properties): the key names the
+    # workload, the split and the band, not the frames in flight
+    # (the band shape, not the launch: a --gpus N line's rank 0 renders band 0
+    # of N, as band 0 of an N-way split emulated on one GPU does)
+    pmc_key = pmc_key_of("c5" if a.config5 else "c3", a.n, W, H, TW, split if group else 0, 0)
+
+    dumped = None
+    if a.dump_outputs and rank == 0:  # the last timed step's frame, before anything renders again
+        dumped = dump_outputs(np, a.dump_outputs, R[(a.steps - 1) % len(R)], with_rgba=not group)
+
+    def result_line(st, bands, more):
+        """The JSON line: the headline of the timed region, the workload and
+        the frame stats `st`; `more` (--full) carries what the passes after
+        the timed region measured, None leaves those keys out."""
+        if a.config5:
+            metric = "frames/sec + Gaussians-splatted/sec at 4K, 8M-Gaussian clustered scene, orbit camera, 1/8 MI355X"
+            workload = (f"synthetic {a.n} Gaussians clustered around point_cloud_12 (sigma 0.02), {W}x{H}, "
+                        f"{TW}x{TW} tiles, orbit camera (120 views), fxy[1]={a.scale_div}")
+        else:
+            metric = HEADLINE_METRIC
+            workload = f"synthetic {a.n} Gaussians, {W}x{H}, {TW}x{TW} tiles, headless camera, fxy[1]={a.scale_div}"
+        if a.split > 1:
+            metric = f"frames/sec, {a.split} row bands emulated on one MI355X (group path, device-copy gather)"
+        if a.fast_exp:
+            metric += " [GS_FLAG_FAST_EXP: RGBA within tolerance, not bit-exact]"
+        if a.sh:
+            metric += " [gs_set_sh: view-dependent SH-3 colour]"
+        if mode == "ranks":
+            par = f"row-band x{world}: one process per GPU, work-balanced contiguous bands, one ncclAllGather/frame"
+        elif mode == "group":
+            par = (f"row-band x{ngpu}: one process, {ngpu} devices (ncclCommInitAll, one host thread per band), "
+                   f"work-balanced contiguous bands, one ncclAllGather/frame")
+        elif mode == "emulated":
+            par = f"row-band x{a.split} emulated on one GPU (copy gather)"
+        else:
+            par = "single GPU"
+        m = more or {}
+        out = {
+            "metric": metric,
+            "value": round(fps, 3),
+            "unit": "frames/s",
+            "gaussians_per_sec": round(fps * a.n, 1),
+            "pairs_per_sec": round(fps * st["n_pairs"], 1),
+            "n_gpus": ngpu,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "prewarm": prewarm,
+            "ms_per_step": round(ms_per_step, 4),
+            "frame_latency_ms": m.get("latency_ms"),
+            "host_enqueue_ms_per_step": round(1e3 * (t_enq - t0) / a.steps, 4),
+            # per-frame enqueue time percentiles (a long tail = the host waited on the GPU)
+            "host_enqueue_ms_p50_p90_max": [round(1e3 * float(np.percentile(enq, q)), 4) for q in (50, 90, 100)],
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic (seeded xoshiro256**, INRIA 3DGS layout"
+                    + (", SH degree 3; parity semantics use DC only)" if a.sh_degree == 3 else ", SH degree 0)"),
+            "config": {
+                "workload": workload,
+                "gaussians": a.n,
+                "resolution": [W, H],
+                "tile": [TW, TW],
+                "frames_in_flight": F,
+                "kernel_table": f"{a.profile_frames} blocking frames, one in flight (stage HIP events)",
+                "parallelism": par,
+                "bands": bands,
+                "pmc_key": pmc_key,
+                # (the last timed frame's binning; a fixed camera's band frames after the first
+                # place their pairs into the layout of that view's last scan: DESIGN.md section 4)
+                "binning": binning_of(int(st["paths"]), bool(st.get("bin_global"))),
+            },
+            "frame": {k: st[k] for k in ("n_rendered", "n_pairs", "n_pairs_binned", "max_list", "n_tiles",
+                                         "n_big_tiles", "paths", "bin_global")},
+            "frame_check": m.get("frame_check"),
+            "end_to_end": m.get("e2e"),
+            "kernels": m.get("kern"),
+            "roofline": m.get("roofline"),
+            "cpu_baseline": m.get("cpu"),
+        }
+        if group and more is not None:
+            out["gather_ms_per_frame"] = m["kern"].get("gather", {}).get("avg_ms")
+            out["group"] = m["ginfo"]
+        if more is None:
+            for k in ("frame_latency_ms", "frame_check", "end_to_end", "kernels", "roofline", "cpu_baseline"):
+                del out[k]
+            del out["config"]["kernel_table"]
+        out["full"] = more is not None
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        return out
+
+    def finish(line):
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        for r in R:
+            r.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not a.full:
+        return finish(result_line(s.stats(), s.bands() if group else None, None))
 
     # the timed frames did the work: each renderer's last timed frame equals a
     # blocking render of the same view on it
@@ -640,11 +794,6 @@ def main():
     # carries the blend's own figure beside it.
     stage = {k: v for k, v in kern.items() if k != "gather"}
     dom = max(stage, key=lambda k: stage[k]["avg_ms"])
-    # PMC counters are per launch (kernel properties): the key names the
-    # workload, the split and the band, not the frames in flight
-    # (the band shape, not the launch: a --gpus N line's rank 0 renders band 0
-    # of N, as band 0 of an N-way split emulated on one GPU does)
-    pmc_key = pmc_key_of("c5" if a.config5 else "c3", a.n, W, H, TW, split if group else 0, 0)
     # HBM bytes per launch of the same stage, from the committed PMC summary of
     # this exact workload and band shape (tools/profile.sh, tools/r6/pmc_bands.sh
     # + tools/pmc_summary.py), if any
@@ -792,80 +941,8 @@ def main():
     if rank == 0 and ngpu == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(a, g, view, proj, W, H, TW, np)
 
-    if rank == 0:
-        if a.config5:
-            metric = "frames/sec + Gaussians-splatted/sec at 4K, 8M-Gaussian clustered scene, orbit camera, 1/8 MI355X"
-            workload = (f"synthetic {a.n} Gaussians clustered around point_cloud_12 (sigma 0.02), {W}x{H}, "
-                        f"{TW}x{TW} tiles, orbit camera (120 views), fxy[1]={a.scale_div}")
-        else:
-            metric = HEADLINE_METRIC
-            workload = f"synthetic {a.n} Gaussians, {W}x{H}, {TW}x{TW} tiles, headless camera, fxy[1]={a.scale_div}"
-        if a.split > 1:
-            metric = f"frames/sec, {a.split} row bands emulated on one MI355X (group path, device-copy gather)"
-        if a.fast_exp:
-            metric += " [GS_FLAG_FAST_EXP: RGBA within tolerance, not bit-exact]"
-        if a.sh:
-            metric += " [gs_set_sh: view-dependent SH-3 colour]"
-        if mode == "ranks":
-            par = f"row-band x{world}: one process per GPU, work-balanced contiguous bands, one ncclAllGather/frame"
-        elif mode == "group":
-            par = (f"row-band x{ngpu}: one process, {ngpu} devices (ncclCommInitAll, one host thread per band), "
-                   f"work-balanced contiguous bands, one ncclAllGather/frame")
-        elif mode == "emulated":
-            par = f"row-band x{a.split} emulated on one GPU (copy gather)"
-        else:
-            par = "single GPU"
-        out = {
-            "metric": metric,
-            "value": round(fps, 3),
-            "unit": "frames/s",
-            "gaussians_per_sec": round(fps * a.n, 1),
-            "pairs_per_sec": round(fps * st["n_pairs"], 1),
-            "n_gpus": ngpu,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "prewarm": prewarm,
-            "ms_per_step": round(ms_per_step, 4),
-            "frame_latency_ms": latency_ms,
-            "host_enqueue_ms_per_step": round(1e3 * (t_enq - t0) / a.steps, 4),
-            # per-frame enqueue time percentiles (a long tail = the host waited on the GPU)
-            "host_enqueue_ms_p50_p90_max": [round(1e3 * float(np.percentile(enq, q)), 4) for q in (50, 90, 100)],
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (seeded xoshiro256**, INRIA 3DGS layout"
-                    + (", SH degree 3; parity semantics use DC only)" if a.sh_degree == 3 else ", SH degree 0)"),
-            "config": {
-                "workload": workload,
-                "gaussians": a.n,
-                "resolution": [W, H],
-                "tile": [TW, TW],
-                "frames_in_flight": F,
-                "kernel_table": f"{a.profile_frames} blocking frames, one in flight (stage HIP events)",
-                "parallelism": par,
-                "bands": bands,
-                "pmc_key": pmc_key,
-                # (the last timed frame's binning; a fixed camera's band frames after the first
-                # place their pairs into the layout of that view's last scan: DESIGN.md section 4)
-                "binning": binning_of(int(st["paths"]), bool(st.get("bin_global"))),
-            },
-            "frame": {k: st[k] for k in ("n_rendered", "n_pairs", "n_pairs_binned", "max_list", "n_tiles",
-                                         "n_big_tiles", "paths", "bin_global")},
-            "frame_check": frame_check,
-            "end_to_end": e2e,
-            "kernels": kern,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-        }
-        if group:
-            out["gather_ms_per_frame"] = kern.get("gather", {}).get("avg_ms")
-            out["group"] = ginfo
-        print(json.dumps(out), flush=True)
-    for r in R:
-        r.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish(result_line(st, bands, {"latency_ms": latency_ms, "frame_check": frame_check, "e2e": e2e, "kern": kern,
+                                   "roofline": roofline, "cpu": cpu, "ginfo": ginfo}))
 
 
 def cpu_baseline(a, g, view, proj, W, H, TW, np):

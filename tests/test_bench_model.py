@@ -265,3 +265,58 @@ def test_binning_named_from_the_frame_paths():
     assert bench.binning_of(bench.PATH_BIN_AGG).startswith("aggregated")
     assert bench.binning_of(bench.PATH_BLEND_PX2).startswith("chunked")
     assert bench.binning_of(0, bin_global=True) == "global atomics"
+
+
+class _FakeRenderer:
+    """The readbacks --dump-outputs takes, from fixed arrays."""
+
+    def __init__(self, rows, width, tiles):
+        import numpy as np
+
+        rng = np.random.default_rng(3)
+        self.bgr = rng.integers(0, 256, (rows, width, 3), dtype=np.uint8)
+        self.rgba = rng.random((rows, width, 4), dtype=np.float32)
+        self.hist = rng.integers(0, 1 << 20, tiles, dtype=np.uint32)
+
+    def get_frame_buffer(self):
+        return self.bgr
+
+    def get_rgba(self):
+        return self.rgba
+
+    def get_histogram(self):
+        return self.hist
+
+
+@pytest.mark.parametrize("rows,width", [(270, 480), (1080, 1920), (2160, 3840)])
+def test_dump_outputs_whole_or_the_same_seeded_sample(tmp_path, rows, width):
+    """--dump-outputs: float32 / float64 .npy files of the renderer's
+    readbacks, whole while they fit the budget (1080p: 58 MB), else (4K) one
+    fixed, seeded sample of the pixels, the same in bgr and rgba and from call
+    to call, named by pixel_index; never more than 64 MB."""
+    import numpy as np
+
+    r = _FakeRenderer(rows, width, 64)
+    shapes = bench.dump_outputs(np, str(tmp_path / "a"), r, with_rgba=True)
+    out = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in shapes}
+    assert all(list(out[k].shape) == shapes[k] for k in out)
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64_000_000
+    np.testing.assert_array_equal(out["histogram"], r.hist)
+    if rows < 2160:
+        assert sorted(out) == ["bgr", "histogram", "rgba"]
+        np.testing.assert_array_equal(out["bgr"], r.bgr)
+        np.testing.assert_array_equal(out["rgba"], r.rgba)
+        return
+    idx = out["pixel_index"].astype(np.int64)
+    # 28 B of bgr + rgba and the 8-B index per sampled pixel, within the budget
+    assert len(idx) == bench.DUMP_BUDGET_BYTES // 36 and (np.diff(idx) > 0).all() and idx[-1] < rows * width
+    np.testing.assert_array_equal(out["bgr"], r.bgr.reshape(-1, 3)[idx])
+    np.testing.assert_array_equal(out["rgba"], r.rgba.reshape(-1, 4)[idx])
+    again = bench.dump_outputs(np, str(tmp_path / "b"), r, with_rgba=False)
+    assert sorted(again) == ["bgr", "histogram", "pixel_index"]  # (a group's line: the gathered BGR8 frame alone)
+    idx_b = np.load(tmp_path / "b" / "pixel_index.npy").astype(np.int64)
+    assert len(idx_b) > len(idx)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "bgr.npy"), r.bgr.reshape(-1, 3)[idx_b])
+    bench.dump_outputs(np, str(tmp_path / "c"), r, with_rgba=True)
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "pixel_index.npy"), out["pixel_index"])

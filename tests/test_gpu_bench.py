@@ -26,7 +26,7 @@ def _bench(*args, timeout=240):
 
 
 def test_bench_in_process_group_over_rccl():
-    d = _bench("--gather", "--n", "200000", "--steps", "60", "--warmup", "20", "--profile-frames", "6",
+    d = _bench("--full", "--gather", "--n", "200000", "--steps", "60", "--warmup", "20", "--profile-frames", "6",
                "--no-cpu-baseline")
     assert d["n_gpus"] == 1
     assert d["value"] > 0 and d["unit"] == "frames/s"
@@ -61,9 +61,44 @@ def test_bench_single_gpu_line_reports_end_to_end():
     """The one-GPU line: `value` from the device-resident frames, and beside it
     the end-to-end rate with every frame's BGR8 read back to pinned host
     memory (the reference's timer includes its readback)."""
-    d = _bench("--n", "200000", "--steps", "60", "--warmup", "20", "--profile-frames", "6", "--e2e-frames", "30",
-               "--no-cpu-baseline")
+    d = _bench("--full", "--n", "200000", "--steps", "60", "--warmup", "20", "--profile-frames", "6",
+               "--e2e-frames", "30", "--no-cpu-baseline")
     assert d["n_gpus"] == 1 and d["value"] > 0
     e = d["end_to_end"]
     assert e["frames"] == 30 and 0 < e["frames_per_s"]
     assert d["roofline"]["traffic_kernels"] == ["gs_blend_px2"]
+
+
+def test_bench_plain_line_and_dumped_outputs(built, tmp_path):
+    """A plain run: --steps sets the timed frames, the line carries the
+    headline fields and ms_per_step and none of --full's passes, and
+    --dump-outputs writes the last timed frame: bit for bit the frame a
+    blocking render of the same seeded scene gives (odd step count: the last
+    step lands on the first of the three renderers in flight)."""
+    import numpy as np
+
+    from gaussian_splat_ipu_amd import camera, scene
+    from gaussian_splat_ipu_amd.splatter import GpuSplatter
+    from gaussian_splat_ipu_amd.tiles import TiledFramebuffer
+
+    d = _bench("--gpus", "1", "--n", "200000", "--steps", "7", "--warmup", "3", "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["full"] is False
+    assert d["value"] > 0 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] == pytest.approx(1e3 / d["value"], rel=1e-3)
+    for k in ("frame_check", "end_to_end", "kernels", "roofline", "cpu_baseline", "frame_latency_ms"):
+        assert k not in d
+    out = {k: np.load(tmp_path / f"{k}.npy") for k in d["dumped_outputs"]}
+    assert sorted(out) == ["bgr", "histogram", "rgba"]
+    assert out["bgr"].dtype == np.float32 and out["rgba"].dtype == np.float32 and out["histogram"].dtype == np.float64
+    assert sum(v.nbytes for v in out.values()) <= 64_000_000
+
+    g, bb = scene.prepare_scene(scene.synthetic(scene.SynthSpec(n=200_000, seed=1, sh_degree=3)))
+    view, proj = camera.headless(bb, 1920, 1080)
+    with GpuSplatter(g, TiledFramebuffer(1920, 1080, 16, 16), device=0) as s:
+        s.set_view_wire(view)
+        s.set_projection_wire(proj)
+        s.update_focal_lengths(camera.FOV_DEFAULT, 1.0)
+        s.execute()
+        np.testing.assert_array_equal(out["bgr"], s.get_frame_buffer().astype(np.float32))
+        np.testing.assert_array_equal(out["rgba"].view(np.uint32), s.get_rgba().view(np.uint32))
+        np.testing.assert_array_equal(out["histogram"], s.get_histogram().astype(np.float64))

@@ -22,7 +22,7 @@ done
 fi
 for r in $(seq 1 ${REPEATS:-3}); do
   for n in $libs; do
-    GSPLAT_LIB=$(path $n) timeout -k 10 300 python bench.py --steps ${STEPS:-600} --no-cpu-baseline ${BENCH_ARGS:-} > $O/bench_${n}_$r.json 2> $O/bench_${n}_$r.err || exit $?
+    GSPLAT_LIB=$(path $n) timeout -k 10 300 python bench.py --full --steps ${STEPS:-600} --no-cpu-baseline ${BENCH_ARGS:-} > $O/bench_${n}_$r.json 2> $O/bench_${n}_$r.err || exit $?
     python3 - "$n" "$O/bench_${n}_$r.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -2,10 +2,11 @@
 # rocprofv3 passes on the bench: kernel trace + stats, then PMC counters in
 # separate passes (never combined with other trace domains).
 #   NAME=c3 BENCH_ARGS="--inflight 1" PASSES="stats fetch write sq1 sq2" STEPS=20
-# Outputs: gpurun_out/prof_$NAME/<pass>/..., gpurun_out/prof_$NAME/<pass>.log
+# Outputs: $OUT_ROOT/prof_$NAME/<pass>/..., $OUT_ROOT/prof_$NAME/<pass>.log
+# (OUT_ROOT defaults to profile_out/, which git ignores)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 export TMPDIR=/tmp
-OUT=gpurun_out/prof_${NAME:-c3}
+OUT=${OUT_ROOT:-profile_out}/prof_${NAME:-c3}
 mkdir -p $OUT
 BENCH="bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-}"
 run() {  # run <name> <timeout> <rocprof args...>

@@ -21,7 +21,7 @@ GSPLAT_LIB=$(lib expm) timeout -k 10 400 python -u -m pytest tests/test_gpu_pari
 tail -n 1 $O/pytest_expm.txt
 for rep in 1 2 3; do
   for v in base expm; do
-    GSPLAT_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --steps 600 --no-cpu-baseline > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err
+    GSPLAT_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --full --steps 600 --no-cpu-baseline > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err
     python3 - $v $O/bench_${v}_$rep.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

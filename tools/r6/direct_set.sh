@@ -42,8 +42,8 @@ done
 SHAPES="bands1 bands2 bands4 bands8" timeout -k 10 900 bash tools/r6/pmc_bands.sh > $O/pmc_bands.txt 2>&1 || { tail -n 20 $O/pmc_bands.txt; exit 1; }
 tail -n 1 $O/pmc_bands.txt
 cp gpurun_out/pmcb/pmc_bands.json $O/pmc_bands.json
-timeout -k 10 300 python3 bench.py --pmc-json $O/pmc_bands.json > $O/bench_default.json 2> $O/bench_default.err
-timeout -k 10 300 python3 bench.py --gather --no-cpu-baseline --pmc-json $O/pmc_bands.json > $O/bench_gather.json 2> $O/bench_gather.err
+timeout -k 10 300 python3 bench.py --full --pmc-json $O/pmc_bands.json > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 300 python3 bench.py --full --gather --no-cpu-baseline --pmc-json $O/pmc_bands.json > $O/bench_gather.json 2> $O/bench_gather.err
 for f in default gather; do python3 - $O/bench_$f.json $f <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ set -e
 timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/pytest_gpu.txt 2>&1 || { tail -n 30 $O/pytest_gpu.txt; exit 1; }
 tail -n 1 $O/pytest_gpu.txt
 timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1 && tail -n 1 $O/smoke.txt
-timeout -k 10 300 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 300 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python3 - $O/bench_default.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -22,11 +22,11 @@ if [ -z "$NO_C5PMC" ]; then
   tail -n 25 $O/pmc_summary_c5.txt | cut -c1-160
   PJ="--pmc-json $O/pmc_all.json"
 fi
-timeout -k 10 300 python3 bench.py $PJ > $O/bench_default.json 2> $O/bench_default.err
-timeout -k 10 300 python3 bench.py --steps 600 $PJ --no-cpu-baseline > $O/bench_600.json 2> $O/bench_600.err
-timeout -k 10 300 python3 bench.py --steps 600 --gather $PJ --no-cpu-baseline > $O/bench_gather.json 2> $O/bench_gather.err
-timeout -k 10 300 python3 bench.py --steps 600 --sh $PJ --no-cpu-baseline > $O/bench_sh.json 2> $O/bench_sh.err
-timeout -k 10 300 python3 bench.py --config5 --steps 240 $PJ > $O/bench_c5.json 2> $O/bench_c5.err
+timeout -k 10 300 python3 bench.py --full $PJ > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 300 python3 bench.py --full --steps 600 $PJ --no-cpu-baseline > $O/bench_600.json 2> $O/bench_600.err
+timeout -k 10 300 python3 bench.py --full --steps 600 --gather $PJ --no-cpu-baseline > $O/bench_gather.json 2> $O/bench_gather.err
+timeout -k 10 300 python3 bench.py --full --steps 600 --sh $PJ --no-cpu-baseline > $O/bench_sh.json 2> $O/bench_sh.err
+timeout -k 10 300 python3 bench.py --full --config5 --steps 240 $PJ > $O/bench_c5.json 2> $O/bench_c5.err
 for f in bench_default bench_600 bench_gather bench_sh bench_c5; do
   python3 - $O/$f.json $f <<'PY'
 import json, sys

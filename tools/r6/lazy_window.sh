@@ -14,7 +14,7 @@ for v in lw2048 lw3072; do
 done
 for rep in 1 2; do
   for v in base lw2048 lw3072; do
-    GSPLAT_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --config5 --steps 240 --no-cpu-baseline > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err
+    GSPLAT_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --full --config5 --steps 240 --no-cpu-baseline > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err
     python3 - $O/bench_${v}_$rep.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
