@@ -186,6 +186,22 @@ class LatticeStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AuxPixel(C.Structure):
+    """gs_aux_pixel: one pixel of the auxiliary planes (24 bytes)."""
+
+    _fields_ = [
+        ("depth_sum", C.c_float),
+        ("coverage", C.c_float),
+        ("depth_median", C.c_float),
+        ("weight_max", C.c_float),
+        ("count", C.c_uint32),
+        ("pick", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class SynthParams(C.Structure):
     _fields_ = [
         ("n", C.c_uint64),
@@ -245,6 +261,10 @@ _SIGS = {
     "gs_kernel_times": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]),
     "gs_reset_kernel_times": (C.c_int, [_P]),
     "gs_set_profile_interval": (C.c_int, [_P, C.c_uint32]),
+    "gs_read_aux32f": (C.c_int, [_P, _FP, C.c_size_t]),
+    "gs_read_aux_ids": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_size_t]),
+    "gs_aux_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    "gs_read_aux_pixel": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(AuxPixel)]),
     "gs_ply_load": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "gs_ply_save": (C.c_int, [_P, C.c_char_p]),
     "gs_ply_free": (None, [_P]),

@@ -140,11 +140,24 @@ struct gs_renderer {
   int ring_head = 0;
   double k_ms[GS_K_COUNT] = {0};
   uint64_t k_launches[GS_K_COUNT] = {0};
+
+  // the auxiliary planes of the last completed frame (gs_aux.hip): per pixel
+  // of the band 4 floats (depth_sum, coverage, depth_median, weight_max), then
+  // 2 words (count, pick); allocated by the first aux call, computed once per
+  // frame (aux_valid: they describe the last enqueued frame)
+  void* d_aux = nullptr;
+  size_t aux_cap_px = 0;  // pixels the allocation holds
+  size_t aux_px = 0;      // pixels of the planes' frame (band rows x width)
+  bool aux_valid = false;
 };
 
 namespace gsr {
 
 int hip_fail(hipError_t e, const char* what);
+int select_device(gs_renderer* r);
+int refuse_moved(const gs_renderer* r, const char* what);
+// the scene's 3D covariances for fp's fxy[1], before a projection that reads them
+int ensure_cov(gs_renderer* r, const gsk::FrameParams& fp, hipStream_t s);
 void poison(void* p, size_t bytes, const char* name);  // GSPLAT_DEBUG_POISON (gs_renderer.hip)
 
 #define GS_HIP(call)                                        \
@@ -173,6 +186,10 @@ int profile_harvest(gs_renderer* r, ProfileSlot& s);
 int read_bins(gs_renderer* r, uint64_t* tile_start, size_t n_start, uint32_t* list, size_t n_list);
 int read_projected(gs_renderer* r, float* dst, size_t n_floats);
 int read_rgba32f(gs_renderer* r, float* dst, size_t n_floats, int layout);
+// the auxiliary planes of the last frame (gs_aux.hip): run the pass if the
+// planes are not that frame's, then read them
+int aux_ensure(gs_renderer* r, const char* what);
+void aux_release(gs_renderer* r);
 // share: a renderer on the same device whose coefficients (set by the same
 // call just before) this one uses instead of uploading its own copy
 int set_sh(gs_renderer* r, const float* f_dc, const float* f_rest, size_t n, int degree,

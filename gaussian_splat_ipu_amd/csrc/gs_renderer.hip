@@ -210,6 +210,7 @@ void release(gs_renderer* r) {
                   r->d_probe})
     if (p) (void)hipFree(p);
   if (r->d_sh && r->owns_sh) (void)hipFree(r->d_sh);
+  aux_release(r);
   free_pairs(r);
   if (r->h_counters) (void)hipHostFree(r->h_counters);
   for (auto& s : r->ring)
@@ -566,6 +567,7 @@ int enqueue_frame(gs_renderer* r) {
   r->last_fp = fp;
   r->have_fp = true;
   r->band_moved = false;
+  r->aux_valid = false;  // (the aux planes are the previous frame's)
   // this frame's band (gs_set_band_rows may have moved it since the last one)
   r->stats.n_tiles = (uint32_t)r->n_tiles;
   r->stats.tiles_y = (uint32_t)r->band_nrows;
@@ -1526,6 +1528,7 @@ int gs_set_band_rows(gs_renderer* r, uint32_t row_begin, uint32_t row_end, uint3
   // would read it with the new band's geometry) until the next frame.
   const int pad = std::max<int>((int)(row_end - row_begin), (int)pad_rows);
   const int rc = gsr::set_band_rows(r, (int)row_begin, (int)row_end, pad);
+  if (rc == GS_OK) r->aux_valid = false;
   if (rc == GS_OK && r->have_fp) {
     r->band_moved = true;
     std::lock_guard<std::mutex> lk(r->hist_mu);

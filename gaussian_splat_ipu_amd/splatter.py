@@ -36,6 +36,7 @@ from ._lib import (
     GS_LAYOUT_REF_TILE_MAJOR,
     GS_LAYOUT_ROW_MAJOR,
     KERNEL_NAMES,
+    AuxPixel,
     CommId,
     Config,
     FrameStats,
@@ -312,6 +313,54 @@ class GpuSplatter:
         out = np.empty((self.n, 12), np.float32)
         check(lib().gs_read_projected(self._h, fptr(out), out.size))
         return out
+
+    # ------------------------------------------------------------ aux planes
+    AUX_F32 = ("depth_sum", "coverage", "depth_median", "weight_max")
+    AUX_IDS = ("count", "pick")
+    PICK_NONE = 0xFFFFFFFF
+
+    def get_aux(self) -> dict:
+        """The last frame's auxiliary planes (gs_read_aux32f, gs_read_aux_ids):
+        six rows x W arrays -- depth_sum, coverage, depth_median, weight_max
+        (float32), count and pick (uint32; pick = the input index of the
+        heaviest contributor, PICK_NONE where nothing contributes).  Computed
+        by a pass of its own on the first call after a frame."""
+        f = np.empty((self.band_rows, self.fb.width, 4), np.float32)
+        u = np.empty((self.band_rows, self.fb.width, 2), np.uint32)
+        check(lib().gs_read_aux32f(self._h, fptr(f), f.size), "gs_read_aux32f")
+        check(lib().gs_read_aux_ids(self._h, u.ctypes.data_as(C.POINTER(C.c_uint32)), u.size), "gs_read_aux_ids")
+        out = {k: np.ascontiguousarray(f[..., i]) for i, k in enumerate(self.AUX_F32)}
+        out.update({k: np.ascontiguousarray(u[..., i]) for i, k in enumerate(self.AUX_IDS)})
+        return out
+
+    def get_depth(self, mode: str = "expected") -> np.ndarray:
+        """rows x W float32 clip-space depth (negative, as the projection's clip
+        z): "expected" = depth_sum / coverage (NaN where nothing contributes),
+        "median" = the depth at which the transmittance passes 0.5 (0 where it
+        never does)."""
+        a = self.get_aux()
+        if mode == "median":
+            return a["depth_median"]
+        if mode != "expected":
+            raise ValueError('get_depth: mode is "expected" or "median"')
+        out = np.full(a["coverage"].shape, np.nan, np.float32)
+        np.divide(a["depth_sum"], a["coverage"], out=out, where=a["coverage"] > 0)
+        return out
+
+    def pick(self, x: int, y: int) -> dict:
+        """The aux planes' values at frame pixel (x, y) (gs_read_aux_pixel):
+        which Gaussian is under the cursor, its weight and the pixel's depth."""
+        px = AuxPixel()
+        check(lib().gs_read_aux_pixel(self._h, int(x), int(y), C.byref(px)), "gs_read_aux_pixel")
+        return px.as_dict()
+
+    def aux_device(self):
+        """(f32 plane pointer, ids plane pointer, pixels): the planes on the
+        device, valid until the next frame (gs_aux_device)."""
+        pf, pu = C.c_void_p(), C.c_void_p()
+        n = C.c_size_t()
+        check(lib().gs_aux_device(self._h, C.byref(pf), C.byref(pu), C.byref(n)), "gs_aux_device")
+        return pf.value, pu.value, n.value
 
     def bgr8_device(self):
         p = C.c_void_p()

@@ -431,6 +431,47 @@ int gs_reset_kernel_times(gs_renderer* r);
  * event costs device time, so throughput runs sample. */
 int gs_set_profile_interval(gs_renderer* r, uint32_t every);
 
+/* ------------------------------------------------------------ auxiliary planes */
+/* The geometry of the last frame: per pixel of the band, over the records
+ * that contribute to it -- the records the blend composites, in list order,
+ * with the blend's own arithmetic (alpha = min(0.99, k3 exp(power)), T' = T (1
+ * - alpha), stop at T' < 1e-4), z = the record's clip z (column 6 of
+ * gs_read_projected, < 0), w = alpha T:
+ *   depth_sum     D = D + (z alpha) T        (the expected depth is D / A)
+ *   coverage      A = A + (1 alpha) T
+ *   depth_median  z of the record that takes T from >= 0.5 to < 0.5 (0: none)
+ *   weight_max    the largest w (0: none)
+ *   count         contributing records
+ *   pick          INPUT index of the record with the largest w (the first of
+ *                 equal ones; 0xFFFFFFFF: none)
+ * Two planes, rows as gs_read_rgba32f's row-major layout (contiguous and
+ * interleaved bands): f32 band_rows x width x 4 (the floats above, in that
+ * order) and u32 band_rows x width x 2 (count, pick).
+ * The planes are computed on demand by a pass of their own over the last
+ * frame (the first aux call after a frame completes the frames in flight,
+ * bins that frame's lists again and walks them; later calls reuse the planes
+ * until the next frame or gs_set_band_rows).  The frame itself, its stats and
+ * its histogram are untouched.  Every value is bit-exact against the CPU
+ * oracle's arithmetic; the pass uses the exact exponential even on a
+ * GS_FLAG_FAST_EXP renderer, whose (approximate) colour frame may therefore
+ * have skipped or stopped differently in a pixel where a test flips.
+ * 24 B per pixel of the band, allocated by the first call (GS_EOOM leaves the
+ * renderer usable).  GS_EINVAL: a null argument, a destination too small, no
+ * frame yet, a band moved since the last frame, a pixel outside the band, a
+ * GS_FLAG_LATTICE renderer, or a row-band group (a group's aux frame is not
+ * provided: create a single renderer for it). */
+int gs_read_aux32f(gs_renderer* r, float* dst, size_t n_floats);    /* rows x W x 4 */
+int gs_read_aux_ids(gs_renderer* r, uint32_t* dst, size_t n_words); /* rows x W x 2 */
+/* The planes' device pointers (synchronous: the pass has run when it
+ * returns); valid until the next frame.  *pixels = band_rows x width. */
+int gs_aux_device(gs_renderer* r, void** f32_dev, void** ids_dev, size_t* pixels);
+typedef struct gs_aux_pixel {
+  float depth_sum, coverage, depth_median, weight_max;
+  uint32_t count, pick;
+} gs_aux_pixel;
+/* One pixel (x, y in frame pixels; y in this renderer's band): 24 bytes back. */
+int gs_read_aux_pixel(gs_renderer* r, uint32_t x, uint32_t y, gs_aux_pixel* out);
+
 /* ------------------------------------------------------------ host-side data path */
 /* PLY / XYZ ingest (src/splat/file_io.cpp:11-77): all 14 3DGS properties are
  * required for .ply (fillPlyProperties); f_rest_* are kept when present. */

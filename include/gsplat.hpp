@@ -99,6 +99,24 @@ class GpuSplatter {
     gs_check(gs_read_tile_histogram(r_, counts.data(), counts.size()), "gs_read_tile_histogram");
   }
 
+  // the last frame's auxiliary planes (no reference counterpart; gsplat.h,
+  // "auxiliary planes"): band rows x width x 4 floats (depth_sum, coverage,
+  // depth_median, weight_max) and x 2 words (count, pick)
+  void getAuxBuffers(std::vector<float>& f32, std::vector<uint32_t>& ids) {
+    const size_t px = (size_t)stats().band_rows * fb_.width;
+    f32.resize(px * 4);
+    ids.resize(px * 2);
+    gs_check(gs_read_aux32f(r_, f32.data(), f32.size()), "gs_read_aux32f");
+    gs_check(gs_read_aux_ids(r_, ids.data(), ids.size()), "gs_read_aux_ids");
+  }
+  // the planes' values at frame pixel (x, y): pick = the input index of the
+  // Gaussian that weighs most there (0xFFFFFFFF: none)
+  gs_aux_pixel pick(uint32_t x, uint32_t y) {
+    gs_aux_pixel p;
+    gs_check(gs_read_aux_pixel(r_, x, y, &p), "gs_read_aux_pixel");
+    return p;
+  }
+
   gs_frame_stats stats() {
     gs_frame_stats st;
     gs_check(gs_get_stats(r_, &st), "gs_get_stats");
